@@ -1,8 +1,16 @@
 """Headline benchmark: GB/s of device-resident chunk decode (shuffle+deflate L4, 1 MiB
 float32 chunks) -- BASELINE.json `metric`, configs[1] (4096-chunk batch per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, weak scaling)
+
+A plain run does only what the headline needs: it builds the seeded corpus, warms up,
+times the K steps and prints the result line.  `--full` adds every other leg (F2, lz4, zstd,
+bitshuffle, the PCIe-inclusive rate, configs[0] / [2] / [3] / [4], the CPU baselines, the
+copy ceiling and the roofline's kernel-event figure); the per-leg switches (`--cfg3 0`,
+`--cpu-seconds 0`, ...) select among them and mean nothing without it.  `--dump-outputs
+DIR` writes what the last timed step left in its output buffers (dump_outputs below); the
+inputs depend on the arguments alone, so two builds can be compared file for file.
 
 `--gpus N` with no WORLD_SIZE in the environment starts the N rank processes itself
 (before anything touches the GPU: children, not exec) on 127.0.0.1 and exits with the
@@ -17,9 +25,10 @@ restatement, which is byte-identical to the reference's storUtil._compress outpu
 seed 20261015 + global chunk index; `--unique` distinct chunks
 per rank are stored several times at distinct HBM addresses.
 
-Prints ONE JSON line on rank 0.  roofline.achieved = (compressed + decoded bytes per
-launch) / inflate-kernel time (HIP events on the launch stream); cpu_baseline = the
-oracle (same c-blosc frame walk + libz inflate) on a bounded sample with 16 threads.
+Prints ONE JSON line on rank 0; ms_per_step is the wall time of one timed step.  With
+`--full`: roofline.achieved = (compressed + decoded bytes per launch) / inflate-kernel
+time (HIP events on the launch stream); cpu_baseline = the oracle (same c-blosc frame
+walk + libz inflate) on a bounded sample with 16 threads.
 """
 import argparse
 import json
@@ -82,7 +91,36 @@ def make_corpus(fmt, n_unique, base_seed, threads):
     return raw, blobs
 
 
-def run_format(fmt, args, dev, rank, world):
+DUMP_SAMPLE_CHUNKS = 48
+
+
+def dump_outputs(dirpath, d_dst, d_st, n, rank, world):
+    """--dump-outputs: what a caller of the timed decode receives -- the decoded chunks and
+    the per-chunk statuses -- as .npy files (about 48 MiB):
+      decoded_sample.npy   float32 (48, 262144): the decoded values of a fixed, seeded sample
+                           of the batch's chunks
+      sample_chunks.npy    float64 (48,): the batch index of each sampled chunk
+      chunk_word_sums.npy  float64 (n,): every chunk's decoded bytes summed as little-endian
+                           int32 words (exact in float64), so no chunk goes unseen
+      status.npy           float64 (n,): the decode status of every chunk
+    Under several ranks each rank writes its own files, suffixed _rank<r>."""
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    pick = np.sort(np.random.default_rng(20261015).choice(n, size=min(n, DUMP_SAMPLE_CHUNKS), replace=False))
+    words = d_dst[:n * CHUNK_BYTES].view(torch.int32).reshape(n, CHUNK_BYTES // 4)
+    sums = torch.cat([words[a:a + 256].sum(dim=1, dtype=torch.int64) for a in range(0, n, 256)])
+    sample = words[torch.from_numpy(pick).to(words.device)].view(torch.float32)
+    np.save(os.path.join(dirpath, f"decoded_sample{sfx}.npy"), sample.cpu().numpy())
+    np.save(os.path.join(dirpath, f"sample_chunks{sfx}.npy"), pick.astype(np.float64))
+    np.save(os.path.join(dirpath, f"chunk_word_sums{sfx}.npy"), sums.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(dirpath, f"status{sfx}.npy"), d_st.cpu().numpy().astype(np.float64))
+
+
+def run_format(fmt, args, dev, rank, world, kernel_event=True, dump=None):
+    """Time args.steps decode launches of one stored format.  kernel_event: one more launch
+    after the timed ones for the inflate kernel's event duration (the roofline figure);
+    dump: directory for dump_outputs, written after the timed steps."""
     import torch
     from hsds_amd.engine import ChunkEngine, pack_chunks
     threads = box_threads()
@@ -106,16 +144,20 @@ def run_format(fmt, args, dev, rank, world):
     def step():
         eng.decode(d_src, d_desc, d_dst, d_st, compressor=comp, shuffle=shuffle, itemsize=4, stream=stream)
 
+    def check():
+        # correctness of what is timed: statuses + sampled chunks vs the raw data
+        st = d_st.cpu().numpy()
+        assert (st == 0).all(), f"decode status errors: {np.unique(st)}"
+        for k in list(range(0, args.chunks, max(1, args.chunks // 8))):
+            o = int(descs[k]["dst_off"])
+            got = d_dst[o:o + CHUNK_BYTES].cpu().numpy()
+            assert np.array_equal(got, raw[order[k]]), f"chunk {k} mismatch"
+
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    # correctness of what is timed: statuses + sampled chunks vs the raw data
-    st = d_st.cpu().numpy()
-    assert (st == 0).all(), f"decode status errors: {np.unique(st)}"
-    for k in list(range(0, args.chunks, max(1, args.chunks // 8))):
-        o = int(descs[k]["dst_off"])
-        got = d_dst[o:o + CHUNK_BYTES].cpu().numpy()
-        assert np.array_equal(got, raw[order[k]]), f"chunk {k} mismatch"
+    if args.warmup:
+        check()
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
@@ -134,12 +176,17 @@ def run_format(fmt, args, dev, rank, world):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
-    if not kern_ms:   # one extra timed launch for the kernel-event duration
+    if not args.warmup:   # nothing ran before the timed steps: their result is checked instead
+        check()
+    if dump:
+        assert ext == args.chunks * CHUNK_BYTES
+        dump_outputs(dump, d_dst, d_st, args.chunks, rank, world)
+    if not kern_ms and kernel_event:   # one extra timed launch for the kernel-event duration
         step()
         torch.cuda.synchronize()
         kern_ms.append(eng.last_inflate_ms())
     res = {"fmt": fmt, "elapsed_s": elapsed, "comp_bytes": comp_bytes, "dec_bytes": dec_bytes,
-           "kernel_ms": float(np.mean(kern_ms)), "blobs": blobs, "raw": raw, "order": order}
+           "kernel_ms": float(np.mean(kern_ms)) if kern_ms else None, "blobs": blobs, "raw": raw, "order": order}
     del d_src, d_dst
     torch.cuda.empty_cache()
     return res
@@ -1207,12 +1254,17 @@ def dry_run_rank(args):
         dist.destroy_process_group()
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--dry-run", type=int, default=0, help="1: rank layout only, gloo, no GPU (CPU tests)")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every other leg (the switches below choose among them), the CPU "
+                         "baselines, the copy ceiling and the roofline figure; off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs as DIR/<name>.npy")
     ap.add_argument("--chunks", type=int, default=4096)
     ap.add_argument("--unique", type=int, default=1024)
     ap.add_argument("--f2", type=int, default=1, help="also measure F2 (HDF5 zlib+shuffle) chunks")
@@ -1242,8 +1294,21 @@ def main():
     ap.add_argument("--max-request-size", type=int, default=100 << 20, help="SN max_request_size (config.yml: 100m)")
     ap.add_argument("--headline", type=int, default=1,
                     help="0: skip the configs[1] headline and print only the selected legs (profiling passes)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        if not args.headline:
+            ap.error("--headline 0 prints only the extra legs: it needs --full")
+        for leg in ("f2", "copy_ceiling", "e2e", "cfg3", "lz4", "bshuf", "cfg1", "zstd", "cfg5", "cfg5w", "cfg4",
+                    "cfg4_full"):
+            setattr(args, leg, 0)
+        args.cpu_seconds = 0.0
+    return args
 
+
+def main():
+    args = parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:], dry_run=bool(args.dry_run)))
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != args.gpus:
@@ -1287,14 +1352,13 @@ def main():
             torch.distributed.destroy_process_group()
         return
 
-    r1 = run_format("F1", args, dev, rank, world)
+    r1 = run_format("F1", args, dev, rank, world, kernel_event=args.full, dump=args.dump_outputs)
     r2 = run_format("F2", args, dev, rank, world) if args.f2 else None
 
     total_dec = r1["dec_bytes"] * world
     ms_per_step = r1["elapsed_s"] / args.steps * 1e3
     value = total_dec * args.steps / r1["elapsed_s"] / 1e9
     launch_bytes = r1["comp_bytes"] + r1["dec_bytes"]
-    achieved = launch_bytes / (r1["kernel_ms"] / 1e3) / 1e9
     out = {
         "metric": "GB/s device-resident chunk decode (shuffle+deflate 1 MiB f32) at 1/2/4/8 GPU",
         "value": round(value, 2),
@@ -1314,16 +1378,18 @@ def main():
                                f"{args.chunks}-chunk batch per GPU, device-resident",
                    "chunks_per_gpu": args.chunks, "chunk_bytes": CHUNK_BYTES,
                    "compressed_bytes_per_gpu": r1["comp_bytes"], "parallelism": f"chunk-sharded x{world}"},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": None,
-                     "kernel": "inflate2_kernel", "kernel_ms": round(r1["kernel_ms"], 3),
-                     "bytes_per_launch": launch_bytes},
     }
+    if r1["kernel_ms"] is not None:   # --full (or --kernel-timing 1): the inflate kernel's own rate
+        achieved = launch_bytes / (r1["kernel_ms"] / 1e3) / 1e9
+        out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": None,
+                           "kernel": "inflate2_kernel", "kernel_ms": round(r1["kernel_ms"], 3),
+                           "bytes_per_launch": launch_bytes}
     if args.copy_ceiling:
         cc = copy_ceiling(dev)
         out["roofline"]["copy_ceiling_GBps"] = max(cc.values())
         out["roofline"]["copy_ceiling"] = cc
-    tr = load_traffic(args, world)
+    tr = load_traffic(args, world) if "roofline" in out else None
     if tr is not None:
         out["roofline"]["traffic"] = tr["bytes_per_launch"]
         out["roofline"]["traffic_undoubled"] = tr.get("bytes_per_launch_undoubled")

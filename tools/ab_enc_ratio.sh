@@ -11,7 +11,7 @@ for spec in "$@"; do
   [ "$chain" != "0" ] && envs+=(HSDS_DEFLATE_CHAIN="$chain")
   [ "$far" = "1" ] && envs+=(HSDS_DEFLATE_FAR=1)
   tag=$(echo "$spec" | tr '/:' '__')
-  env "${envs[@]}" timeout -k 10 300 python bench.py --headline 0 --steps 3 --warmup 1 --cpu-seconds 0 \
+  env "${envs[@]}" timeout -k 10 300 python bench.py --full --headline 0 --steps 3 --warmup 1 --cpu-seconds 0 \
     --cfg3 0 --cfg1 0 --cfg5 1 --cfg4-full 0 --f2 0 --e2e 0 --lz4 0 --zstd 0 --bshuf 0 --cfg5w 0 --cfg4 0 > gpurun_out/aber_$tag.log 2>&1
   rc=$?; [ $rc -eq 0 ] || { echo "$spec rc=$rc"; tail -5 gpurun_out/aber_$tag.log; exit $rc; }
   python - "$spec" gpurun_out/aber_$tag.log <<'PY'

@@ -7,7 +7,7 @@ i=0
 for e in "$@"; do
   i=$((i+1))
   [ "$e" = "-" ] && e=""
-  env $e timeout -k 10 300 python bench.py --steps 5 --warmup 1 --cpu-seconds 0 --e2e 0 --cfg3 0 --cfg5 0 --lz4 0 --zstd 0 --bshuf 0 --cfg1 0 --cfg5w 0 --cfg4 0 --cfg4-full 0 \
+  env $e timeout -k 10 300 python bench.py --full --steps 5 --warmup 1 --cpu-seconds 0 --e2e 0 --cfg3 0 --cfg5 0 --lz4 0 --zstd 0 --bshuf 0 --cfg1 0 --cfg5w 0 --cfg4 0 --cfg4-full 0 \
     > gpurun_out/abenv_$i.log 2>&1
   rc=$?; [ $rc -eq 0 ] || { echo "[$e] rc=$rc"; tail -5 gpurun_out/abenv_$i.log; exit $rc; }
   python - "$e" gpurun_out/abenv_$i.log <<'PY'
