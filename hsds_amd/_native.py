@@ -66,6 +66,38 @@ class PlanGeom(ctypes.Structure):
                 ("step", ctypes.c_int64 * MAX_RANK), ("slab_base", ctypes.c_int64)]
 
 
+POINT_MAX_SEGS = 16
+
+
+class PointGeom(ctypes.Structure):
+    _fields_ = [("rank", ctypes.c_int32), ("itemsize", ctypes.c_int32), ("dims", ctypes.c_uint64 * MAX_RANK),
+                ("layout", ctypes.c_uint64 * MAX_RANK)]
+
+
+class PointSeg(ctypes.Structure):
+    _fields_ = [("chunk_off", ctypes.c_int32), ("out_off", ctypes.c_int32), ("nbytes", ctypes.c_int32)]
+
+
+def point_geom(dims, layout, itemsize):
+    """hsds_point_geom of a dataset extent and its chunk layout"""
+    rank = len(dims)
+    if rank < 1 or rank > MAX_RANK or len(layout) != rank:
+        raise ValueError(f"point selections take rank 1..{MAX_RANK} and a layout of the same rank")
+    g = PointGeom()
+    g.rank, g.itemsize = rank, int(itemsize)
+    for d in range(rank):
+        g.dims[d], g.layout[d] = int(dims[d]), int(layout[d])
+    return g
+
+
+def point_segs(segs):
+    """(chunk_off, out_off, nbytes) tuples -> a C array of hsds_point_seg"""
+    arr = (PointSeg * max(len(segs), 1))()
+    for k, (c, o, n) in enumerate(segs):
+        arr[k].chunk_off, arr[k].out_off, arr[k].nbytes = int(c), int(o), int(n)
+    return arr
+
+
 _lib = None
 
 
@@ -110,6 +142,9 @@ def lib():
         "hsds_host_map": (I, [P, P, U64, ctypes.POINTER(ctypes.c_void_p)]),
         "hsds_host_unmap": (I, [P, P]),
         "hsds_stage_upload": (I, [P, P, P, P, I64, P, P, U64, I, P]),
+        "hsds_points_locate": (I, [P, P, P, I64, P, P, P, P]),
+        "hsds_points_gather": (I, [P, P, P, P, P, I64, P, I, I, I, P, P, P, P]),
+        "hsds_points_scatter": (I, [P, P, P, P, P, P, I64, P, I, I, I, P, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

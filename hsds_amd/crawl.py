@@ -889,3 +889,90 @@ class PagedReader:
     def close(self):
         if self.mode == "direct":
             self.host.close()
+
+
+# ---- point selections ------------------------------------------------------------------
+class PointPlan:
+    """The SN's plan of a point request (dset_lib.py:459-484, chunk_sn.py:467-545): every
+    point's chunk (ONE locate launch instead of getChunkId per point), the distinct chunks
+    with their owners (getObjPartition through partition_ids) and, per rank, the request
+    positions of the points whose chunk it owns, in request order.  Every rank builds the
+    same plan from the same request.  A point outside the extent raises ValueError
+    (chunk_sn.py:486-523: HTTPBadRequest)."""
+
+    def __init__(self, dset_id, dims, layout, points, dtype, world, device=None):
+        import torch
+        from .engine import ChunkEngine
+        self.dset_id = dset_id
+        self.dims = tuple(int(d) for d in dims)
+        self.layout = tuple(int(c) for c in layout)
+        self.dtype = np.dtype(dtype)
+        self.world = int(world)
+        rank = len(self.dims)
+        points = np.asarray(points)
+        if points.dtype != np.dtype("uint64"):
+            raise ValueError("unexpected dtype for point array")
+        if points.ndim != 2 or points.shape[1] != rank or len(self.layout) != rank:
+            raise ValueError("unexpected shape for point array")
+        self.points = np.ascontiguousarray(points)
+        self.n = len(points)
+        eng = ChunkEngine(device)
+        d_pts = torch.from_numpy(self.points.view(np.int64)).to(eng.device)
+        chunk, _, nbad = eng.locate_points(d_pts, self.dims, self.layout, self.dtype.itemsize)
+        uniq, which = torch.unique(chunk, return_inverse=True)
+        if int(nbad.item()):
+            raise ValueError(f"{int(nbad.item())} point(s) outside the dataset extent")
+        grid = [-(-d // c) for d, c in zip(self.dims, self.layout)]
+        lin = uniq.cpu().numpy()
+        self.idx = np.stack(np.unravel_index(lin, grid), axis=1).astype(np.int64) if lin.size else \
+            np.zeros((0, rank), np.int64)
+        prefix = "c-" + dset_id[2:] + "_"
+        self.ids = [prefix + "_".join(str(i) for i in row) for row in self.idx.tolist()]
+        self.owner = partition_ids(prefix, self.idx, self.world)
+        # request positions per rank (stable: request order within a rank)
+        pt_owner = torch.from_numpy(self.owner.astype(np.int64)).to(eng.device)[which] if self.n else \
+            torch.zeros(0, dtype=torch.int64, device=eng.device)
+        self.by_rank = [torch.nonzero(pt_owner == r).reshape(-1) for r in range(self.world)]
+
+    def chunk_ids(self, rank):
+        return [cid for cid, o in zip(self.ids, self.owner) if o == rank]
+
+
+class ShardedPointReader:
+    """One rank of a sharded point read: its store gathers the points whose chunk it owns
+    and places them at their request positions in the response buffer -- a device tensor, or
+    an engine.HostBuffer that every rank of the node maps (the "no gather" shape of
+    ShardedReader: no exchange between the GPUs)."""
+
+    def __init__(self, plan, rank, store):
+        self.plan, self.rank, self.store = plan, rank, store
+
+    def read(self, response, filter_ops=None, fill_value=None, select_dt=None):
+        """place this rank's values into `response`; returns how many points it served"""
+        import torch
+        mine = self.plan.by_rank[self.rank]
+        if not mine.numel():
+            return 0
+        pts = torch.from_numpy(self.plan.points.view(np.int64)).to(mine.device)[mine]
+        self.store.get_points(self.plan.dset_id, self.plan.dims, self.plan.layout, pts, self.plan.dtype,
+                              filter_ops=filter_ops, fill_value=fill_value, select_dt=select_dt, dst=response,
+                              dst_index=mine)
+        return int(mine.numel())
+
+
+class ShardedPointWriter:
+    """One rank of a sharded point write: the points whose chunk it owns, in request order
+    (so a repeated point keeps its last value), through its store's put_points."""
+
+    def __init__(self, plan, rank, store):
+        self.plan, self.rank, self.store = plan, rank, store
+
+    def write(self, values, filter_ops=None, fill_value=None):
+        """`values`: the request's (n,) values; returns the chunk ids this rank touched"""
+        mine = self.plan.by_rank[self.rank]
+        if not mine.numel():
+            return []
+        sel = mine.cpu().numpy()
+        return self.store.put_points(self.plan.dset_id, self.plan.dims, self.plan.layout, self.plan.points[sel],
+                                     np.asarray(values)[sel], self.plan.dtype, filter_ops=filter_ops,
+                                     fill_value=fill_value)

@@ -15,6 +15,10 @@
 //  hyperslab copies (chunkUtil.py:882-995, chunk_crawl.py:118-150,395-418)
 //   copy_kernel / compare_kernel   strided N-d region copies / numpy-equal compares
 //   plan_descs_kernel   one thread per piece: copy records of a hyperslab plan
+//  point selections (chunkUtil.py:998-1148, dset_lib.py:459-484; points.h)
+//   points_locate_kernel   one thread per point: chunk index and element offset
+//   points_gather_kernel   one lane per 16-byte destination slot (or per point)
+//   points_scatter_kernel  one lane per sorted entry, the last of equal keys writes
 //  encode (storUtil._compress, storUtil.py:238-281)
 //   enc_plan_kernel     one thread per chunk: c-blosc 1.21 frame geometry, one item per split
 //   parse_kernel        persistent waves, one zlib / LZ stream each: hash chains + parse
@@ -46,6 +50,7 @@
 #include "bshuf.h"
 #include "zstd_enc.h"
 #include "region.h"
+#include "points.h"
 
 #ifndef HZ_ZSTD_WPE
 #define HZ_ZSTD_WPE 4      // zstd_kernel waves per SIMD the compiler must allow (VGPR budget)
@@ -789,6 +794,23 @@ __global__ void __launch_bounds__(256) compare_kernel(const uint8_t* __restrict_
 
 __global__ void zero_i32_kernel(int32_t* p, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = 0;
+}
+
+
+// ---- point selections (points.h) ---------------------------------------------------
+__global__ void __launch_bounds__(256) points_locate_kernel(hsds_point_geom g, const uint64_t* __restrict__ pts, int64_t n,
+                                                            int64_t* __restrict__ chunk, int64_t* __restrict__ eoff,
+                                                            int32_t* nbad) {
+  pt::locate_thread(g, pts, n, chunk, eoff, nbad, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                    (uint64_t)gridDim.x * blockDim.x);
+}
+
+__global__ void __launch_bounds__(256) points_gather_kernel(pt::GatherArgs a) {
+  pt::gather_thread(a, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, (uint64_t)gridDim.x * blockDim.x);
+}
+
+__global__ void __launch_bounds__(256) points_scatter_kernel(pt::ScatterArgs a) {
+  pt::scatter_thread(a, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, (uint64_t)gridDim.x * blockDim.x);
 }
 
 
@@ -2412,6 +2434,77 @@ int hsds_plan_descs(hsds_engine* e, const hsds_plan_geom* geom, const int64_t* d
   const int tpb = 256;
   hipLaunchKernelGGL(plan_descs_kernel, dim3((unsigned)((n + tpb - 1) / tpb)), dim3(tpb), 0, (hipStream_t)stream, g,
                      d_tabs, d_piece, d_poff, d_coff, n, d_out);
+  return hipGetLastError() == hipSuccess ? HSDS_OK : HSDS_ERR_DEVICE;
+}
+
+// ---- point selections ---------------------------------------------------------
+// blocks of 256 threads, one unit per thread up to 8192 blocks (32 per CU), then grid-stride
+static unsigned points_grid(uint64_t units) {
+  const uint64_t b = (units + 255u) / 256u;
+  return (unsigned)(b < 1 ? 1 : b > 8192 ? 8192 : b);
+}
+
+static int points_segs(const hsds_point_seg* segs, int nsegs, int chunk_elem, int out_elem, pt::Segs& g) {
+  if (!segs || nsegs < 1 || nsegs > HSDS_POINT_MAX_SEGS) return 0;
+  g.n = nsegs;
+  g.out_elem = out_elem;
+  for (int k = 0; k < HSDS_POINT_MAX_SEGS; k++) g.s[k] = k < nsegs ? segs[k] : hsds_point_seg{0, 0, 0};
+  return pt::segs_ok(g, chunk_elem);
+}
+
+int hsds_points_locate(hsds_engine* e, const hsds_point_geom* geom, const uint64_t* d_points, int64_t n,
+                       int64_t* d_chunk, int64_t* d_eoff, int32_t* d_nbad, void* stream) {
+  if (!e || !geom || n < 0) return HSDS_ERR_ARG;
+  const hsds_point_geom g = *geom;
+  if (g.rank < 1 || g.rank > HSDS_MAX_RANK || g.itemsize < 1) return HSDS_ERR_ARG;
+  for (int d = 0; d < g.rank; d++)
+    if (g.layout[d] < 1) return HSDS_ERR_ARG;
+  if (n == 0) return HSDS_OK;
+  if (!d_points || !d_chunk || !d_eoff || !d_nbad) return HSDS_ERR_ARG;
+  if (hipSetDevice(e->device) != hipSuccess) return HSDS_ERR_DEVICE;
+  hipLaunchKernelGGL(points_locate_kernel, dim3(points_grid((uint64_t)n)), dim3(256), 0, (hipStream_t)stream, g,
+                     d_points, n, d_chunk, d_eoff, d_nbad);
+  return hipGetLastError() == hipSuccess ? HSDS_OK : HSDS_ERR_DEVICE;
+}
+
+int hsds_points_gather(hsds_engine* e, const void* d_arena, const int64_t* d_slot, const int64_t* d_which,
+                       const int64_t* d_eoff, int64_t n, const hsds_point_seg* segs, int nsegs, int chunk_elem,
+                       int out_elem, const void* d_fill, void* d_out, const int64_t* d_dst_index, void* stream) {
+  if (!e || n < 0) return HSDS_ERR_ARG;
+  pt::GatherArgs a;
+  if (!points_segs(segs, nsegs, chunk_elem, out_elem, a.segs)) return HSDS_ERR_ARG;
+  if (n == 0) return HSDS_OK;
+  if (!d_arena || !d_slot || !d_eoff || !d_out) return HSDS_ERR_ARG;
+  a.arena = (const uint8_t*)d_arena;
+  a.slot = d_slot;
+  a.which = d_which;
+  a.eoff = d_eoff;
+  a.n = n;
+  a.fill = (const uint8_t*)d_fill;
+  a.out = (uint8_t*)d_out;
+  a.dst_index = d_dst_index;
+  if (hipSetDevice(e->device) != hipSuccess) return HSDS_ERR_DEVICE;
+  hipLaunchKernelGGL(points_gather_kernel, dim3(points_grid(pt::gather_units(a))), dim3(256), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? HSDS_OK : HSDS_ERR_DEVICE;
+}
+
+int hsds_points_scatter(hsds_engine* e, void* d_arena, const int64_t* d_slot, const int64_t* d_which,
+                        const int64_t* d_eoff, const int64_t* d_order, int64_t n, const hsds_point_seg* segs,
+                        int nsegs, int chunk_elem, int out_elem, const void* d_vals, void* stream) {
+  if (!e || n < 0) return HSDS_ERR_ARG;
+  pt::ScatterArgs a;
+  if (!points_segs(segs, nsegs, chunk_elem, out_elem, a.segs)) return HSDS_ERR_ARG;
+  if (n == 0) return HSDS_OK;
+  if (!d_arena || !d_slot || !d_eoff || !d_vals) return HSDS_ERR_ARG;
+  a.arena = (uint8_t*)d_arena;
+  a.slot = d_slot;
+  a.which = d_which;
+  a.eoff = d_eoff;
+  a.order = d_order;
+  a.n = n;
+  a.vals = (const uint8_t*)d_vals;
+  if (hipSetDevice(e->device) != hipSuccess) return HSDS_ERR_DEVICE;
+  hipLaunchKernelGGL(points_scatter_kernel, dim3(points_grid((uint64_t)n)), dim3(256), 0, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? HSDS_OK : HSDS_ERR_DEVICE;
 }
 

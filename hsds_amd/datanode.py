@@ -1173,6 +1173,184 @@ class ChunkStore:
             raise err
         return out
 
+    # ---- point selections (POST_Chunk with points, chunk_dn.py:758-807) ---------------
+    def _locate(self, dset_id, dims, chunk_dims, points, itemsize):
+        """upload `points` (n x rank uint64: host array or device tensor) and locate them:
+        (which, eoff, chunk index rows of the distinct chunks, their ids, nbad) -- only the
+        short list of distinct chunks (and the out-of-extent count) comes back to the host"""
+        import torch
+        dev = self.cache.arena.buf.device
+        rank = len(dims)
+        if len(chunk_dims) != rank:
+            raise ValueError("chunk layout doesn't match rank")
+        if isinstance(points, torch.Tensor):
+            d_pts = points.contiguous()
+        else:
+            points = np.asarray(points)
+            if points.dtype != np.dtype("uint64"):
+                raise ValueError("unexpected dtype for point array")
+            if points.ndim != 2 or points.shape[1] != rank:
+                raise ValueError("unexpected shape for point array")
+            d_pts = torch.from_numpy(np.ascontiguousarray(points).view(np.int64)).to(dev)
+        chunk, eoff, nbad = self.reader.eng.locate_points(d_pts, dims, chunk_dims, itemsize)
+        uniq, which = torch.unique(chunk, return_inverse=True)
+        lin = uniq.cpu().numpy()
+        bad = int(nbad.item())
+        grid = [-(-int(d) // int(c)) for d, c in zip(dims, chunk_dims)]
+        good = lin[lin >= 0]
+        idx = np.stack(np.unravel_index(good, grid), axis=1).astype(np.int64) if good.size else \
+            np.zeros((0, rank), np.int64)
+        prefix = "c-" + dset_id[2:] + "_"
+        ids = [prefix + "_".join(str(i) for i in row) for row in idx.tolist()]
+        return which, eoff, idx, ids, bad
+
+    @_locked
+    def get_points(self, dset_id, dims, chunk_dims, points, dtype, filter_ops=None, fill_value=None, select_dt=None,
+                   dst=None, dst_index=None):
+        """A point read over many chunks at once: the SN's per-point chunk lookup
+        (dset_lib.py:459-484), its per-chunk POST_Chunk requests (chunk_crawl.py:422-530)
+        and every DN's chunkReadPoints (chunkUtil.py:998-1061) as ONE locate launch, one
+        chunk batch and ONE gather launch.  `points`: n x rank uint64 dataset coordinates
+        (host array or device tensor).  The distinct chunks are read through the cache
+        (hits from HBM, misses decoded as one batch); a chunk with no stored object gives
+        its points the fill value (or zeros) and nothing is cached for it.  Returns the
+        (n,) values as a uint8 device tensor of n * itemsize bytes (dtype, or select_dt's
+        fields only), or writes them into `dst` (uint8 device tensor or engine.HostBuffer)
+        when given -- value i at element position dst_index[i] (int64, host or device)
+        instead of i, which is how a rank of a sharded read places its points into the
+        shared response; `dst` must hold n elements (max(dst_index) + 1 with dst_index),
+        else ValueError.  A point outside the extent raises ValueError, a stored object
+        that fails to decode HTTPInternalServerError, before anything is returned.
+        The gather is queued on the current stream and runs in request order with a
+        contiguous output (the measured choice: DESIGN.md "Point selections").  The host
+        waits for the device only when stored objects were decoded: when every chunk was a
+        cache hit the call returns with the gather still queued, so the bytes of a
+        HostBuffer `dst` (read by the host, not by a later kernel of the stream) are valid
+        once the caller has synchronised that stream."""
+        import torch
+        from .partition import getS3Key
+        from .selection import point_segments
+        dtype = np.dtype(dtype)
+        chunk_dims = tuple(int(c) for c in chunk_dims)
+        segs, out_dt = point_segments(dtype, select_dt)
+        E = out_dt.itemsize
+        abase = self.cache.arena.buf
+        dev = abase.device
+        which, eoff, idx, ids, bad = self._locate(dset_id, dims, chunk_dims, points, dtype.itemsize)
+        if bad:
+            raise ValueError(f"{bad} point(s) outside the dataset extent")
+        n = eoff.numel()
+        if dst_index is not None and not isinstance(dst_index, torch.Tensor):
+            dst_index = torch.from_numpy(np.ascontiguousarray(dst_index, np.int64)).to(dev)
+        if dst_index is not None and dst_index.numel() != n:
+            raise ValueError(f"{dst_index.numel()} dst_index entries for {n} points")
+        if dst is not None:
+            # the gather writes where it is told: check the caller's buffer before the launch
+            room = (dst.nbytes if hasattr(dst, "d_ptr") else dst.numel() * dst.element_size()) // E
+            if dst_index is None:
+                need = n
+            elif n:
+                lo, hi = (int(v) for v in torch.aminmax(dst_index))
+                if lo < 0:
+                    raise ValueError("negative dst_index")
+                need = hi + 1
+            else:
+                need = 0
+            if need > room:
+                raise ValueError(f"dst holds {room} elements of {E} bytes, the request needs {need}")
+        out = dst if dst is not None else torch.empty(n * E, dtype=torch.uint8, device=dev)
+        if n == 0:
+            return out
+        reads = [ChunkRead(cid, getS3Key(cid)) for cid in ids]
+        vals, finish = self.get_chunks_deferred(reads, dtype, chunk_dims, filter_ops=filter_ops,
+                                                fill_value=fill_value, views=False)
+        try:
+            # chunk addresses: cache slots by their arena offsets, uncached reads (a full
+            # cache) by their batch tensor; one base below them all, so offsets are >= 0
+            ptrs = []
+            for r, v in zip(reads, vals):
+                if v is None or isinstance(v, Exception):
+                    ptrs.append(None)
+                elif v is RESIDENT:
+                    ptrs.append(abase.data_ptr() + self.cache._lru[r.chunk_id].off)
+                else:
+                    ptrs.append(v.data_ptr())
+            base = min([p for p in ptrs if p is not None], default=abase.data_ptr())
+            slot = torch.from_numpy(np.array([-1 if p is None else p - base for p in ptrs], np.int64)).to(dev)
+            d_fill = None
+            if fill_value is not None:
+                one = np.zeros(1, dtype)
+                one[...] = fill_value
+                pat = np.zeros(E, np.uint8)
+                for c, o, nb in segs:
+                    pat[o:o + nb] = one.view(np.uint8)[c:c + nb]
+                if pat.any():
+                    d_fill = torch.from_numpy(pat).to(dev)
+            self.reader.eng.gather_points(base, slot, which, eoff, segs, dtype.itemsize, E, out,
+                                          fill=d_fill, dst_index=dst_index)
+            if finish.reads_pending:
+                torch.cuda.current_stream(dev).synchronize()
+        except BaseException:
+            finish.abort()
+            raise
+        for v in finish():
+            if isinstance(v, Exception):
+                raise v
+        return out
+
+    @_locked
+    def put_points(self, dset_id, dims, chunk_dims, points, values, dtype, filter_ops=None, fill_value=None):
+        """A point write over many chunks at once (chunk_sn.py:467-545, chunk_crawl.py:533-605,
+        chunk_dn.py:758-782 with chunkUtil.chunkWritePoints, chunkUtil.py:1064-1148).
+        `points`: n x rank uint64 dataset coordinates; `values`: (n,) host array of `dtype`,
+        or of a compound with fewer fields (those fields are updated).  A point outside the
+        extent raises ValueError before anything is fetched or written (the SN's 400).
+        Every touched chunk is made resident (get_chunk with chunk_init), ONE scatter launch
+        applies the points in request order (a repeated point keeps its last value), and
+        every touched chunk is marked dirty: the reference calls save_chunk without a
+        compare.  Returns the touched chunk ids."""
+        import torch
+        from .partition import getS3Key
+        from .selection import point_segments
+        dtype = np.dtype(dtype)
+        chunk_dims = tuple(int(c) for c in chunk_dims)
+        values = np.asarray(values)
+        subset = len(values.dtype) > 0 and len(values.dtype) < len(dtype)
+        segs, val_dt = point_segments(dtype, values.dtype if subset else None)
+        values = np.ascontiguousarray(values if values.dtype == val_dt else values.astype(val_dt)).reshape(-1)
+        abase = self.cache.arena.buf
+        dev = abase.device
+        which, eoff, idx, ids, bad = self._locate(dset_id, dims, chunk_dims, points, dtype.itemsize)
+        if bad:
+            raise ValueError(f"{bad} point(s) outside the dataset extent")
+        n = eoff.numel()
+        if values.size != n:
+            raise ValueError(f"{values.size} values for {n} points")
+        if n == 0:
+            return []
+        reads = [ChunkRead(cid, getS3Key(cid)) for cid in ids]
+        self._resident(reads, dtype, chunk_dims, filter_ops, fill_value)    # (raises a read's own error)
+        pinned = []
+        try:
+            for r in reads:
+                node = self.cache._lru.get(r.chunk_id)
+                if node is None:
+                    raise MemoryError("chunk cache cannot hold the write batch")
+                node.pinned += 1
+                pinned.append(r.chunk_id)
+            slot = torch.from_numpy(np.array([self.cache._lru[r.chunk_id].off for r in reads], np.int64)).to(dev)
+            d_vals = torch.from_numpy(values.view(np.uint8).reshape(-1).copy()).to(dev)
+            chunk_bytes = int(np.prod(chunk_dims, dtype=np.int64)) * dtype.itemsize
+            order = torch.sort(which * chunk_bytes + eoff, stable=True)[1]
+            self.reader.eng.scatter_points(abase, slot, which, eoff, order, segs, dtype.itemsize, val_dt.itemsize,
+                                           d_vals)
+        finally:
+            for key in pinned:
+                self.cache.unpin(key)
+        for r in reads:
+            self.cache.setDirty(r.chunk_id)
+        return ids
+
     @_locked
     def encode_dirty(self, filter_ops, stream=None):
         """The device half of flush for a dataset with a Blosc compressor (no bitshuffle):

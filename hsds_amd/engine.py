@@ -220,6 +220,56 @@ class ChunkEngine:
             raise nat.NativeError(rc, "hsds_compare_batch")
         return copy_descs
 
+    def locate_points(self, points, dims, layout, itemsize, chunk=None, eoff=None, nbad=None, stream=None):
+        """Asynchronous chunk lookup of `points` (n x rank uint64 device tensor of dataset
+        coordinates): returns (chunk, eoff, nbad) device tensors -- the C-order linear index
+        of each point's chunk in the grid ceil(dims / layout) (-1: outside the extent), the
+        byte offset of its element inside the chunk array, and the int32 count of points
+        outside the extent (added to `nbad` when given)."""
+        if points.dtype != torch.uint64 and points.dtype != torch.int64:
+            raise ValueError("points are a uint64 device tensor")
+        rank = len(dims)
+        n = points.numel() // max(rank, 1)
+        if points.numel() != n * rank or not points.is_contiguous():
+            raise ValueError("points are n x rank, C-contiguous")
+        geom = nat.point_geom(dims, layout, itemsize)
+        dev = points.device
+        chunk = torch.empty(n, dtype=torch.int64, device=dev) if chunk is None else chunk
+        eoff = torch.empty(n, dtype=torch.int64, device=dev) if eoff is None else eoff
+        nbad = torch.zeros(1, dtype=torch.int32, device=dev) if nbad is None else nbad
+        rc = nat.lib().hsds_points_locate(self.eng.h, ctypes.byref(geom), _ptr(points), n, _ptr(chunk), _ptr(eoff),
+                                          _ptr(nbad), _stream_handle(stream))
+        if rc != nat.OK:
+            raise nat.NativeError(rc, "hsds_points_locate")
+        return chunk, eoff, nbad
+
+    def gather_points(self, arena, slot, which, eoff, segs, chunk_elem, out_elem, out, fill=None, dst_index=None,
+                      n=None, stream=None):
+        """Asynchronous element gather: output element i of `out` (a uint8 device tensor or
+        a HostBuffer; position dst_index[i] when given) = the `segs` bytes ((chunk_off,
+        out_off, nbytes) tuples) of the chunk element at arena + slot[which[i]] + eoff[i];
+        a negative slot gives `fill` (out_elem bytes on the device, None: zeros).  `arena`
+        may be a raw device address (the slots of chunks in several allocations are offsets
+        from the lowest of them)."""
+        n = eoff.numel() if n is None else int(n)
+        base = arena if isinstance(arena, int) else _ptr(arena)      # (an int: a raw device address)
+        rc = nat.lib().hsds_points_gather(self.eng.h, base, _ptr(slot), _ptr(which), _ptr(eoff), n,
+                                          nat.point_segs(segs), len(segs), int(chunk_elem), int(out_elem),
+                                          _ptr(fill), _ptr(out), _ptr(dst_index), _stream_handle(stream))
+        if rc != nat.OK:
+            raise nat.NativeError(rc, "hsds_points_gather")
+
+    def scatter_points(self, arena, slot, which, eoff, order, segs, chunk_elem, out_elem, vals, n=None, stream=None):
+        """Asynchronous element scatter: the `segs` bytes of value i (vals + i * out_elem)
+        go to the chunk element at arena + slot[which[i]] + eoff[i].  `order`: the point
+        indices stably sorted by (which, eoff); of equal keys the last entry writes."""
+        n = eoff.numel() if n is None else int(n)
+        rc = nat.lib().hsds_points_scatter(self.eng.h, _ptr(arena), _ptr(slot), _ptr(which), _ptr(eoff), _ptr(order),
+                                           n, nat.point_segs(segs), len(segs), int(chunk_elem), int(out_elem),
+                                           _ptr(vals), _stream_handle(stream))
+        if rc != nat.OK:
+            raise nat.NativeError(rc, "hsds_points_scatter")
+
     def unshuffle(self, src, dst, itemsize, stream=None):
         rc = nat.lib().hsds_unshuffle_device(self.eng.h, _ptr(src), src.numel(), int(itemsize), _ptr(dst),
                                              _stream_handle(stream))

@@ -682,3 +682,154 @@ def chunkWriteSelection(chunk_arr=None, slices=None, data=None):
     if updated:
         np.copyto(arr, d_chunk.cpu().numpy().view(arr.dtype).reshape(arr.shape))
     return updated
+
+
+# ---- point selections (POST_Chunk with points, chunk_dn.py:758-807) -----------------
+def point_segments(dset_dt, select_dt=None):
+    """The segment table of a point read / write (hsds_point_seg: chunk_off, out_off,
+    nbytes) and the request-side element dtype.  No select_dt, or one with as many fields
+    as the dataset's: the whole element -- one segment, or one per field when the compound
+    has padding bytes (numpy moves structured elements field by field: padding bytes read
+    as zeros and are left alone by a write).  Fewer fields: one segment per named field
+    (chunk field offset <-> select_dt field offset).  Neighbouring segments merge."""
+    dset_dt = np.dtype(dset_dt)
+    subset = select_dt is not None and len(np.dtype(select_dt)) < len(dset_dt)
+    if subset:
+        select_dt = np.dtype(select_dt)
+        raw = []
+        for f in select_dt.names or ():
+            if f not in dset_dt.names:
+                raise ValueError(f"no field of name {f}")
+            if select_dt.fields[f][0] != dset_dt.fields[f][0]:
+                raise NotImplementedError("field selection with a converted field type")
+            raw.append((dset_dt.fields[f][1], select_dt.fields[f][1], dset_dt.fields[f][0].itemsize))
+        if not raw:
+            raise ValueError("select_dt names no field")
+        out_dt = select_dt
+    else:
+        out_dt = dset_dt
+        raw = [(0, 0, dset_dt.itemsize)]
+        if dset_dt.names and sum(fdt.itemsize for _, fdt, _ in _fields(dset_dt)) < dset_dt.itemsize:
+            raw = [(off, off, fdt.itemsize) for _, fdt, off in _fields(dset_dt)]
+    segs = []
+    for c, o, n in sorted(raw, key=lambda s: s[1]):
+        if segs and segs[-1][0] + segs[-1][2] == c and segs[-1][1] + segs[-1][2] == o:
+            segs[-1] = (segs[-1][0], segs[-1][1], segs[-1][2] + n)
+        else:
+            segs.append((c, o, n))
+    if len(segs) > nat.POINT_MAX_SEGS:
+        if subset:
+            raise NotImplementedError(f"a field subset of more than {nat.POINT_MAX_SEGS} separate byte runs")
+        segs = [(0, 0, dset_dt.itemsize)]      # (a padded compound of that many fields moves with its padding)
+    return segs, out_dt
+
+
+def _locate_in_chunk(chunk_id, shape, itemsize, pts, what):
+    """the engine and the element byte offsets (device int64) of the dataset points `pts` (n x rank uint64,
+    host) inside chunk `chunk_id`; IndexError for a point before the chunk's corner
+    (getChunkRelativePoint) or past the chunk (numpy's own IndexError in the reference)"""
+    import torch
+    from .engine import ChunkEngine
+    idx = getChunkIndex(chunk_id)
+    rank = len(shape)
+    if len(idx) != rank:
+        raise ValueError("chunk id rank does not match the chunk array")
+    corner = np.array([i * c for i, c in zip(idx, shape)], np.uint64)
+    if (pts < corner).any() or (pts >= corner + np.array(shape, np.uint64)).any():
+        raise IndexError(f"{what}: point outside chunk {chunk_id}")
+    # every point is inside the chunk: located over a dataset that ends where the chunk ends,
+    # the kernel's element offsets are the chunk-relative ones (no wait for the device)
+    eng = ChunkEngine()
+    d_pts = torch.from_numpy(np.ascontiguousarray(pts).view(np.int64)).to(eng.device)
+    _, eoff, _ = eng.locate_points(d_pts, [(i + 1) * c for i, c in zip(idx, shape)], shape, itemsize)
+    return eng, eoff
+
+
+def chunkReadPoints(chunk_id=None, chunk_layout=None, chunk_arr=None, point_arr=None, select_dt=None):
+    """chunkUtil.chunkReadPoints (chunkUtil.py:998-1061): the elements of `chunk_arr` at the
+    dataset coordinates `point_arr` (uint64, n x rank) as an (n,) array of select_dt (the
+    chunk dtype, or a compound with fewer fields: those fields only), gathered on the GPU
+    in one launch instead of one Python iteration per point.  Same ValueError cases as the
+    reference; IndexError for a point outside the chunk.  The chunk array has the layout's
+    shape (every DN chunk does)."""
+    import torch
+    arr = np.asarray(chunk_arr)
+    rank = arr.ndim
+    if rank == 0:
+        raise ValueError("No dimension passed to chunk read points")
+    if len(chunk_layout) != rank:
+        raise ValueError("chunk layout doesn't match rank")
+    point_arr = np.asarray(point_arr)
+    if point_arr.dtype != np.dtype("uint64"):
+        raise ValueError("unexpected dtype for point array")
+    if point_arr.ndim != 2 or point_arr.shape[1] != rank:
+        raise ValueError("unexpected shape for point array")
+    if tuple(arr.shape) != tuple(int(c) for c in chunk_layout):
+        raise ValueError("chunk array shape differs from the chunk layout")
+    dt = arr.dtype
+    segs, out_dt = point_segments(dt, select_dt)
+    n = point_arr.shape[0]
+    out = np.zeros((n,), out_dt)
+    if n == 0:
+        return out
+    eng, eoff = _locate_in_chunk(chunk_id, arr.shape, dt.itemsize, point_arr, "chunkReadPoints")
+    d_chunk = _to_dev(arr, eng.device)
+    d_out = torch.empty(out.nbytes, dtype=torch.uint8, device=eng.device)
+    slot = torch.zeros(1, dtype=torch.int64, device=eng.device)
+    eng.gather_points(d_chunk, slot, None, eoff, segs, dt.itemsize, out_dt.itemsize, d_out)
+    out.view(np.uint8).reshape(-1)[:] = d_out.cpu().numpy()
+    return out
+
+
+def chunkWritePoints(chunk_id=None, chunk_layout=None, chunk_arr=None, point_arr=None, select_dt=None):
+    """chunkUtil.chunkWritePoints (chunkUtil.py:1064-1148): `point_arr` holds records
+    (coord | value) -- coord uint64 (a (rank,) array for rank > 1), value of select_dt (the
+    chunk dtype, or a compound with fewer fields) -- assigned to `chunk_arr` in order: of a
+    repeated point the last value stands.  One scatter launch on the GPU.  A field subset
+    updates the named fields (the reference pairs the subset's values with the dataset's
+    field names by position, which is right for a prefix of the fields only).  A point
+    outside the chunk raises IndexError and nothing is written (the reference has applied
+    the points before it by then)."""
+    import torch
+    arr = chunk_arr
+    rank = arr.ndim
+    if rank == 0:
+        raise ValueError("No dimension passed to chunkWritePoints")
+    point_arr = np.asarray(point_arr)
+    if point_arr.ndim != 1:
+        raise ValueError("Expected point array to be one dimensional")
+    dt = arr.dtype
+    sdt = dt if select_dt is None else np.dtype(select_dt)
+    comp = point_arr.dtype
+    if len(comp) != 2:
+        raise ValueError("expected compound type for point array")
+    dt_0, dt_1 = comp[0], comp[1]
+    if dt_0.base != np.dtype("uint64"):
+        raise ValueError("unexpected dtype for point array")
+    if rank == 1:
+        if dt_0.shape:
+            raise ValueError("unexpected dtype for point array")
+    else:
+        if dt_0.shape[0] != rank:
+            raise ValueError("unexpected shape for point array")
+        if dt_1 != sdt:
+            raise ValueError("unexpected dtype for point array")
+    if not arr.flags["C_CONTIGUOUS"]:
+        raise ValueError("chunk arrays are C-contiguous")
+    if tuple(arr.shape) != tuple(int(c) for c in chunk_layout):
+        raise ValueError("chunk array shape differs from the chunk layout")
+    segs, val_dt = point_segments(dt, sdt if len(sdt) < len(dt) else None)
+    n = len(point_arr)
+    if n == 0:
+        return
+    pts = np.ascontiguousarray(point_arr[comp.names[0]]).reshape(n, rank)
+    vals = np.ascontiguousarray(point_arr[comp.names[1]])
+    if vals.dtype != val_dt:
+        vals = vals.astype(val_dt)             # (rank 1: the reference lets numpy cast the value)
+    eng, eoff = _locate_in_chunk(chunk_id, arr.shape, dt.itemsize, pts, "chunkWritePoints")
+    d_chunk = _to_dev(arr, eng.device)
+    d_vals = _to_dev(vals, eng.device)
+    order = torch.sort(eoff, stable=True)[1]
+    slot = torch.zeros(1, dtype=torch.int64, device=eng.device)
+    eng.scatter_points(d_chunk, slot, None, eoff, order, segs, dt.itemsize, val_dt.itemsize, d_vals)
+    np.copyto(arr, d_chunk.cpu().numpy().view(dt).reshape(arr.shape))

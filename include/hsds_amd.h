@@ -23,6 +23,10 @@
  *   hsds_encode_bitshuffle_batch / hsds_bitshuffle_compress / hsds_bitshuffle_bound
  *                        <- storUtil.py:94-131 _shuffle(codec=2, ...) (bitshuffle.compress_lz4 behind
  *                           the 12-byte header), reached from _compress(shuffle=2) (storUtil.py:243-251)
+ *   hsds_points_locate   <- hsds/dset_lib.py:459-484 (chunkUtil.getChunkId per point) and
+ *                           chunkUtil.py:793 getChunkRelativePoint
+ *   hsds_points_gather   <- chunkUtil.py:998 chunkReadPoints, chunk_crawl.py:422-530 (placement by point index)
+ *   hsds_points_scatter  <- chunkUtil.py:1064 chunkWritePoints
  *
  * Threading: an engine is bound to one device and is re-entrant: its calls may come from
  * any host threads (a DN running them off the event loop in a thread pool).  Calls that
@@ -208,6 +212,61 @@ typedef struct {
 int hsds_plan_descs(hsds_engine* e, const hsds_plan_geom* geom, const int64_t* d_tabs, const int64_t* d_piece,
                     const int64_t* d_poff, const int64_t* d_coff, int64_t n, hsds_copy_desc* d_out,
                     void* stream);
+
+/* ---- point selections -------------------------------------------------------------
+ * Coordinate lists (POST_Chunk with points: chunk_dn.py:758-807) over chunks resident in
+ * device memory.  All three calls are asynchronous on `stream`. */
+typedef struct {
+  int32_t rank;                          /* 1 .. HSDS_MAX_RANK                          */
+  int32_t itemsize;                      /* bytes per dataset element                   */
+  uint64_t dims[HSDS_MAX_RANK];          /* dataset extent                              */
+  uint64_t layout[HSDS_MAX_RANK];        /* chunk layout (every entry >= 1)             */
+} hsds_point_geom;
+
+/* One run of selected bytes of an element: bytes [chunk_off, chunk_off + nbytes) of the
+ * chunk element <-> bytes [out_off, out_off + nbytes) of the request-side element.  A table
+ * has 1 .. HSDS_POINT_MAX_SEGS entries sorted by out_off that do not overlap: one entry of
+ * itemsize bytes for a whole element, one per field for a compound field subset. */
+typedef struct {
+  int32_t chunk_off;
+  int32_t out_off;
+  int32_t nbytes;
+} hsds_point_seg;
+#define HSDS_POINT_MAX_SEGS 16
+
+/* The per-point chunk lookup of the SN (hsds/dset_lib.py:459-484 with chunkUtil.getChunkId,
+ * chunkUtil.py:353-371: coord // layout per dimension) and chunkUtil.getChunkRelativePoint
+ * (chunkUtil.py:793-810), for n points at once: d_points holds n x rank uint64 dataset
+ * coordinates; d_chunk[i] gets the C-order linear index of point i's chunk in the chunk
+ * grid ceil(dims / layout) and d_eoff[i] the byte offset of its element inside the chunk
+ * array (layout dims, C order).  A point with a coordinate >= its extent (compared
+ * unsigned) gets d_chunk[i] = -1, d_eoff[i] = 0 and adds one to *d_nbad (the caller zeroes
+ * it). */
+int hsds_points_locate(hsds_engine* e, const hsds_point_geom* geom, const uint64_t* d_points, int64_t n,
+                       int64_t* d_chunk, int64_t* d_eoff, int32_t* d_nbad, void* stream);
+
+/* chunkUtil.chunkReadPoints (chunkUtil.py:998-1061: one Python iteration per point) over
+ * many chunks at once, and the SN's np_arr[point_index[i]] placement
+ * (chunk_crawl.py:422-530): output element i (out_elem bytes) at d_out + d_dst_index[i] *
+ * out_elem (d_dst_index == NULL: i) takes the table's segments from the chunk element at
+ * d_arena + d_slot[d_which[i]] + d_eoff[i]; bytes of the output element that no segment
+ * covers are zero.  d_which == NULL: every point in d_slot[0].  A negative slot (or
+ * d_which[i]): no such chunk, the element is d_fill's out_elem bytes (NULL: zeros), the 404
+ * case of chunk_crawl.py:505-517.  chunk_elem = bytes per chunk element (table bounds). */
+int hsds_points_gather(hsds_engine* e, const void* d_arena, const int64_t* d_slot, const int64_t* d_which,
+                       const int64_t* d_eoff, int64_t n, const hsds_point_seg* segs, int nsegs, int chunk_elem,
+                       int out_elem, const void* d_fill, void* d_out, const int64_t* d_dst_index, void* stream);
+
+/* chunkUtil.chunkWritePoints (chunkUtil.py:1064-1148) over many chunks at once: the table's
+ * segments of value i (d_vals + i * out_elem) go to the chunk element at d_arena +
+ * d_slot[d_which[i]] + d_eoff[i]; every other byte of the chunk element is left alone.
+ * d_order holds the point indices 0 .. n-1 stably sorted by (d_which, d_eoff) (NULL: the
+ * points are already in that order); of several entries with one key only the last writes,
+ * so the last request position wins as in the reference's in-order loop.  Points of a
+ * negative slot are skipped. */
+int hsds_points_scatter(hsds_engine* e, void* d_arena, const int64_t* d_slot, const int64_t* d_which,
+                        const int64_t* d_eoff, const int64_t* d_order, int64_t n, const hsds_point_seg* segs,
+                        int nsegs, int chunk_elem, int out_elem, const void* d_vals, void* stream);
 
 /* ---- host response buffers (the "no gather" sharded read) ---------
  * The SN streams each page of a GET_Value to the client (chunk_sn.py:1085-1135): the
