@@ -98,6 +98,30 @@ def point_segs(segs):
     return arr
 
 
+QUERY_MAX_OPS, QUERY_POOL, QUERY_MAX_ISIN = 32, 256, 1024
+Q_CONST, Q_CMP, Q_CMP_FIELD, Q_CMP_BYTES, Q_ISIN, Q_AND, Q_OR = range(7)
+Q_EQ, Q_NE, Q_LT, Q_LE, Q_GT, Q_GE = range(6)
+Q_DOM_I64, Q_DOM_U64, Q_DOM_F64, Q_DOM_SU = range(4)
+Q_KIND_S = 10
+
+
+class QueryOp(ctypes.Structure):
+    _fields_ = [("op", ctypes.c_uint8), ("cmp", ctypes.c_uint8), ("dom", ctypes.c_uint8), ("kind", ctypes.c_uint8),
+                ("kind_b", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 3), ("off", ctypes.c_int32),
+                ("off_b", ctypes.c_int32), ("len", ctypes.c_int32), ("len_b", ctypes.c_int32),
+                ("imm", ctypes.c_uint64)]
+
+
+class QueryProg(ctypes.Structure):
+    _fields_ = [("nops", ctypes.c_int32), ("reserved", ctypes.c_int32), ("ops", QueryOp * QUERY_MAX_OPS),
+                ("pool", ctypes.c_uint8 * QUERY_POOL)]
+
+
+# hsds_query_chunk as a numpy record (the table is built on the host and uploaded)
+QUERY_CHUNK_FIELDS = [("slot", "<i8"), ("first", "<i8"), ("count", "<i8"), ("step", "<i8"), ("index0", "<i8"),
+                      ("word0", "<i8")]
+assert ctypes.sizeof(QueryOp) == 32 and ctypes.sizeof(QueryProg) == 8 + 32 * QUERY_MAX_OPS + QUERY_POOL
+
 _lib = None
 
 
@@ -145,6 +169,8 @@ def lib():
         "hsds_points_locate": (I, [P, P, P, I64, P, P, P, P]),
         "hsds_points_gather": (I, [P, P, P, P, P, I64, P, I, I, I, P, P, P, P]),
         "hsds_points_scatter": (I, [P, P, P, P, P, P, I64, P, I, I, I, P, P]),
+        "hsds_query_mask": (I, [P, P, P, I64, I64, I, P, P, I64, P, P, P]),
+        "hsds_query_emit": (I, [P, P, P, I64, I64, I, P, P, I64, P, I, I, P, P, I, I, P, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

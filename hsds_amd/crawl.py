@@ -976,3 +976,57 @@ class ShardedPointWriter:
         return self.store.put_points(self.plan.dset_id, self.plan.dims, self.plan.layout, self.plan.points[sel],
                                      np.asarray(values)[sel], self.plan.dtype, filter_ops=filter_ops,
                                      fill_value=fill_value)
+
+
+class QueryPlan:
+    """The SN's plan of a query request (dset_lib.py:384-424 and 600-653, chunk_crawl.py
+    :700-740): the chunks of the selection in dataset order with their owners (getObjPartition
+    through partition_ids).  Every rank runs ChunkStore.query over its own chunks
+    (`query(rank, store)`), and `merge` puts the ranks' per-chunk row blocks back in dataset
+    order on the host and applies the limit -- the results are variable-size and bound for
+    the host response, so there is no exchange between the GPUs.  The merged limit is the
+    first `limit` matches in dataset order; the reference stops launching chunks once enough
+    hits came back (chunk_crawl.py:722), so its rows depend on which chunk answers first."""
+
+    def __init__(self, dset_id, dims, layout, selection, query, dtype, world, select_dt=None, limit=0):
+        from .selection import getChunkIds, getChunkIndex
+        if len(dims) != 1 or len(layout) != 1:
+            raise ValueError("Query operations only supported on one-dimensional datasets")
+        self.dset_id, self.dims, self.layout = dset_id, (int(dims[0]),), (int(layout[0]),)
+        self.selection, self.query_text, self.dtype = selection, query, np.dtype(dtype)
+        self.select_dt, self.limit, self.world = select_dt, int(limit), int(world)
+        sel = selection[0] if selection else slice(0, self.dims[0], 1)
+        start, stop, step = sel.indices(self.dims[0])
+        self.ids = getChunkIds(dset_id, [slice(start, stop, step)], self.layout) if start < stop else []
+        idx = np.array([getChunkIndex(cid) for cid in self.ids], np.int64).reshape(len(self.ids), 1)
+        self.owner = partition_ids("c-" + dset_id[2:] + "_", idx, self.world)
+
+    def chunk_ids(self, rank):
+        return [cid for cid, o in zip(self.ids, self.owner) if o == rank]
+
+    def query(self, rank, store, filter_ops=None, query_update=None):
+        """this rank's share: ChunkStore.query over the chunks it owns.  Each rank keeps up
+        to `limit` rows: the merged first `limit` can need no more of any one rank."""
+        return store.query(self.dset_id, self.dims, self.layout, self.selection, self.query_text, self.dtype,
+                           filter_ops=filter_ops, select_dt=self.select_dt, limit=self.limit,
+                           query_update=query_update, chunk_ids=self.chunk_ids(rank))
+
+    def merge(self, results, limit=None):
+        """per-rank QueryResults (None for a rank that owns no chunk) -> the response array in
+        dataset order, at most `limit` rows (default: the plan's)"""
+        limit = self.limit if limit is None else int(limit)
+        blocks, dt = {}, None
+        for res in results:
+            if res is None:
+                continue
+            dt = res.dtype
+            rows = res.rows.cpu().numpy().view(dt)
+            kept = np.minimum(res.starts, len(rows))          # (a rank's own limit cut its tail)
+            for k, cid in enumerate(res.chunk_ids):
+                blocks[cid] = rows[kept[k]:kept[k + 1]]
+        if dt is None:
+            from .query import query_segments
+            dt = query_segments(self.dtype, self.select_dt)[1]
+        out = [blocks[cid] for cid in self.ids if cid in blocks and len(blocks[cid])]
+        merged = np.concatenate(out) if out else np.zeros(0, dt)
+        return merged[:limit] if limit > 0 else merged

@@ -19,6 +19,9 @@
 //   points_locate_kernel   one thread per point: chunk index and element offset
 //   points_gather_kernel   one lane per 16-byte destination slot (or per point)
 //   points_scatter_kernel  one lane per sorted entry, the last of equal keys writes
+//  query selections (chunkUtil.py:1375-1569, chunk_dn.py:192-240; query.h)
+//   query_mask_kernel   one lane per selected row: the predicate program, a ballot per 64 rows
+//   query_emit_kernel   one lane per row: rank from the scanned counts, update, response record
 //  encode (storUtil._compress, storUtil.py:238-281)
 //   enc_plan_kernel     one thread per chunk: c-blosc 1.21 frame geometry, one item per split
 //   parse_kernel        persistent waves, one zlib / LZ stream each: hash chains + parse
@@ -51,6 +54,7 @@
 #include "zstd_enc.h"
 #include "region.h"
 #include "points.h"
+#include "query.h"
 
 #ifndef HZ_ZSTD_WPE
 #define HZ_ZSTD_WPE 4      // zstd_kernel waves per SIMD the compiler must allow (VGPR budget)
@@ -811,6 +815,19 @@ __global__ void __launch_bounds__(256) points_gather_kernel(pt::GatherArgs a) {
 
 __global__ void __launch_bounds__(256) points_scatter_kernel(pt::ScatterArgs a) {
   pt::scatter_thread(a, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, (uint64_t)gridDim.x * blockDim.x);
+}
+
+// ---- query selections (query.h) ------------------------------------------------------
+// blocks of 256 threads = four waves, a wave per mask word (all 64 lanes of a wave share w
+// and loop the same number of times, so the ballot sees the whole word)
+__global__ void __launch_bounds__(256) query_mask_kernel(qy::MaskArgs a) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, T = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t w = t >> 6; w < (uint64_t)a.nwords; w += T >> 6) qy::mask_word(a, (int64_t)w, (uint32_t)(t & 63u));
+}
+
+__global__ void __launch_bounds__(256) query_emit_kernel(qy::EmitArgs a) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, T = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t w = t >> 6; w < (uint64_t)a.nwords; w += T >> 6) qy::emit_row(a, (int64_t)w, (uint32_t)(t & 63u));
 }
 
 
@@ -2505,6 +2522,58 @@ int hsds_points_scatter(hsds_engine* e, void* d_arena, const int64_t* d_slot, co
   a.vals = (const uint8_t*)d_vals;
   if (hipSetDevice(e->device) != hipSuccess) return HSDS_ERR_DEVICE;
   hipLaunchKernelGGL(points_scatter_kernel, dim3(points_grid((uint64_t)n)), dim3(256), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? HSDS_OK : HSDS_ERR_DEVICE;
+}
+
+// ---- query selections -----------------------------------------------------------
+int hsds_query_mask(hsds_engine* e, const void* d_arena, const hsds_query_chunk* d_chunks, int64_t nchunks,
+                    int64_t nwords, int rowsize, const hsds_query_prog* prog, const void* d_isin, int64_t isin_bytes,
+                    uint64_t* d_mask, int32_t* d_count, void* stream) {
+  if (!e || nchunks < 0 || nwords < 0 || !prog || isin_bytes < 0) return HSDS_ERR_ARG;
+  if (!qy::prog_ok(*prog, rowsize, d_isin ? isin_bytes : 0)) return HSDS_ERR_ARG;
+  if (nwords == 0) return HSDS_OK;
+  if (!d_arena || !d_chunks || nchunks < 1 || !d_mask || !d_count) return HSDS_ERR_ARG;
+  qy::MaskArgs a;
+  a.arena = (const uint8_t*)d_arena;
+  a.chunks = d_chunks;
+  a.nchunks = nchunks;
+  a.nwords = nwords;
+  a.rowsize = rowsize;
+  a.isin = (const uint8_t*)d_isin;
+  a.mask = d_mask;
+  a.count = d_count;
+  a.prog = *prog;
+  if (hipSetDevice(e->device) != hipSuccess) return HSDS_ERR_DEVICE;
+  hipLaunchKernelGGL(query_mask_kernel, dim3(points_grid((uint64_t)nwords * 64u)), dim3(256), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? HSDS_OK : HSDS_ERR_DEVICE;
+}
+
+int hsds_query_emit(hsds_engine* e, void* d_arena, const hsds_query_chunk* d_chunks, int64_t nchunks,
+                    int64_t nwords, int rowsize, const uint64_t* d_mask, const int64_t* d_base, int64_t limit,
+                    const hsds_point_seg* segs, int nsegs, int out_elem, void* d_out,
+                    const hsds_point_seg* upd_segs, int n_upd_segs, int upd_elem, const void* d_upd, void* stream) {
+  if (!e || nchunks < 0 || nwords < 0 || limit < 0) return HSDS_ERR_ARG;
+  qy::EmitArgs a;
+  if (!points_segs(segs, nsegs, rowsize, out_elem, a.segs) || a.segs.s[0].out_off < 8) return HSDS_ERR_ARG;
+  a.upd = nullptr;
+  a.upd_segs = a.segs;
+  if (upd_segs) {
+    if (!d_upd || !points_segs(upd_segs, n_upd_segs, rowsize, upd_elem, a.upd_segs)) return HSDS_ERR_ARG;
+    a.upd = (const uint8_t*)d_upd;
+  }
+  if (nwords == 0) return HSDS_OK;
+  if (!d_arena || !d_chunks || nchunks < 1 || !d_mask || !d_base || !d_out) return HSDS_ERR_ARG;
+  a.arena = (uint8_t*)d_arena;
+  a.chunks = d_chunks;
+  a.nchunks = nchunks;
+  a.nwords = nwords;
+  a.rowsize = rowsize;
+  a.mask = d_mask;
+  a.base = d_base;
+  a.limit = limit;
+  a.out = (uint8_t*)d_out;
+  if (hipSetDevice(e->device) != hipSuccess) return HSDS_ERR_DEVICE;
+  hipLaunchKernelGGL(query_emit_kernel, dim3(points_grid((uint64_t)nwords * 64u)), dim3(256), 0, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? HSDS_OK : HSDS_ERR_DEVICE;
 }
 

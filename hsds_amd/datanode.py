@@ -35,6 +35,8 @@ from .codec import BIT_SHUFFLE_BLOCK, HTTPInternalServerError
 # HDF5 file chunk location (rangegetUtil.py:9): index = hyper-chunk index tuple,
 # offset / length = byte range in the HDF5 file
 ChunkLocation = namedtuple("ChunkLocation", ["index", "offset", "length"])
+# what ChunkStore.query returns
+QueryResult = namedtuple("QueryResult", ["rows", "dtype", "chunk_ids", "starts", "touched"])
 
 H5D_CONTIGUOUS_REF = "H5D_CONTIGUOUS_REF"
 
@@ -1350,6 +1352,120 @@ class ChunkStore:
         for r in reads:
             self.cache.setDirty(r.chunk_id)
         return ids
+
+    # ---- query selections (GET_Chunk / PUT_Chunk with query=, chunk_dn.py:192-240, 499-545) ------
+    @_locked
+    def query(self, dset_id, dims, chunk_dims, selection, query, dtype, filter_ops=None, select_dt=None, limit=0,
+              query_update=None, chunk_ids=None):
+        """A where-clause query over many chunks at once: the SN's per-chunk GET_Chunk /
+        PUT_Chunk requests with query= (chunk_crawl.py:700-740, dset_lib.py:600-653) and
+        every DN's chunkQuery (chunkUtil.py:1375-1569) as ONE mask launch, one scan and ONE
+        emit launch over all the chunks of `selection` (a list of one slice, None: every
+        row) of the 1-D compound dataset.  The chunks (selection.getChunkIds; only those
+        also in `chunk_ids` when given: a rank's share) are read through the cache: hits
+        from HBM, misses decoded as one batch, and a chunk with no stored object has no rows
+        (a query does no chunk_init, chunk_dn.py:177).
+        Returns QueryResult(rows, dtype, chunk_ids, starts, touched): the response records
+        (uint8 device tensor; `dtype` = getQueryDtype(select_dt): the uint64 dataset index,
+        then the selected fields) in dataset order -- with limit > 0 the FIRST `limit`
+        matches in dataset order, where the reference's cross-chunk limit depends on which
+        chunk answers first; starts[k] = matches (before the limit) in chunk_ids[:k].
+        query_update {field: value}: the matched rows under the limit get those values in
+        the cache, are returned as updated, and the chunks with at least one such row are
+        marked dirty and listed in `touched`; no chunk is created for a missing object.
+        A stored object that fails to decode raises HTTPInternalServerError before anything
+        is updated or returned, and leaves nothing pinned."""
+        import torch
+        from .partition import getS3Key
+        from .selection import getChunkIds
+        from . import query as qry
+        dtype = np.dtype(dtype)
+        if len(dims) != 1 or len(chunk_dims) != 1:
+            raise ValueError("Query operations only supported on one-dimensional datasets")
+        n, c = int(dims[0]), int(chunk_dims[0])
+        if selection is not None and len(selection) != 1:
+            raise ValueError("Selection rank does not match shape rank")
+        sel = selection[0] if selection else slice(0, n, 1)
+        if sel.step is not None and sel.step < 1:
+            raise ValueError("query selections have a positive step")
+        start, stop, step = sel.indices(n)
+        cq = qry.compile_query(query, dtype)
+        upd_segs, upd = None, None
+        if query_update:
+            if cq.where_field:
+                raise ValueError("query update is not supported with where in")
+            upd_segs, upd = qry.update_record(dtype, query_update)
+        segs, rsp_dt = qry.query_segments(dtype, select_dt)
+        abase = self.cache.arena.buf
+        dev = abase.device
+        ids = getChunkIds(dset_id, [slice(start, stop, step)], (c,)) if start < stop else []
+        if chunk_ids is not None:
+            keep = set(chunk_ids)
+            ids = [cid for cid in ids if cid in keep]
+        rows = []                     # (first, count, step, index0) per chunk
+        for cid in ids:
+            lo = int(cid[cid.rfind("_") + 1:]) * c
+            first = start if start >= lo else start + -(-(lo - start) // step) * step
+            rows.append((first - lo, len(range(first, min(stop, lo + c), step)), step, lo))
+        empty = QueryResult(torch.empty(0, dtype=torch.uint8, device=dev), rsp_dt, ids,
+                            np.zeros(len(ids) + 1, np.int64), [])
+        if not ids:
+            return empty
+        reads = [ChunkRead(cid, getS3Key(cid)) for cid in ids]
+        vals, finish = self.get_chunks_deferred(reads, dtype, (c,), filter_ops=filter_ops, views=False)
+        pinned, finished = [], False
+        try:
+            if upd is not None:
+                # an update writes the cache: every read has to be known good before the launch
+                if finish.reads_pending:
+                    torch.cuda.current_stream(dev).synchronize()
+                finished = True
+                vals = finish()
+                for v in vals:
+                    if isinstance(v, Exception):
+                        raise v
+                ptrs = []
+                for r, v in zip(reads, vals):
+                    node = None if v is None else self.cache._lru.get(r.chunk_id)
+                    if v is not None and node is None:
+                        raise MemoryError("chunk cache cannot hold the query update")
+                    if node is not None:
+                        node.pinned += 1
+                        pinned.append(r.chunk_id)
+                    ptrs.append(None if node is None else abase.data_ptr() + node.off)
+            else:
+                ptrs = []
+                for r, v in zip(reads, vals):
+                    if v is None or isinstance(v, Exception):
+                        ptrs.append(None)
+                    elif v is RESIDENT:
+                        ptrs.append(abase.data_ptr() + self.cache._lru[r.chunk_id].off)
+                    else:
+                        ptrs.append(v.data_ptr())
+            base = min([p for p in ptrs if p is not None], default=abase.data_ptr())
+            table = [(-1 if p is None else p - base,) + row for p, row in zip(ptrs, rows)]
+            d_upd = None if upd is None else torch.from_numpy(upd).to(dev)
+            out, starts = self.reader.eng.query(base, table, dtype.itemsize, cq.prog, cq.isin, segs, rsp_dt.itemsize,
+                                                limit=limit, upd_segs=upd_segs,
+                                                upd_elem=0 if upd is None else len(upd), upd=d_upd)
+        except BaseException:
+            if not finished:
+                finish.abort()
+            raise
+        finally:
+            for key in pinned:
+                self.cache.unpin(key)
+        touched = []
+        if upd is None:
+            for v in finish():
+                if isinstance(v, Exception):
+                    raise v
+        else:
+            cap = np.minimum(starts, limit) if limit and limit > 0 else starts
+            touched = [cid for k, cid in enumerate(ids) if cap[k + 1] > cap[k]]
+            for cid in touched:
+                self.cache.setDirty(cid)
+        return QueryResult(out, rsp_dt, ids, starts, touched)
 
     @_locked
     def encode_dirty(self, filter_ops, stream=None):

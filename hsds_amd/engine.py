@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .query import query_chunk_table
 
 CHUNK_DESC_DTYPE = np.dtype([("src_off", "<u8"), ("src_len", "<u8"), ("dst_off", "<u8"), ("dst_len", "<u8")])
 COPY_DESC_DTYPE = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("src_stride", "<i8", (nat.MAX_RANK,)),
@@ -269,6 +270,68 @@ class ChunkEngine:
                                            _ptr(vals), _stream_handle(stream))
         if rc != nat.OK:
             raise nat.NativeError(rc, "hsds_points_scatter")
+
+    def query_mask(self, arena, chunks, nchunks, nwords, rowsize, prog, isin, mask, count, stream=None):
+        """Asynchronous mask pass of a query (hsds_query_mask): `chunks` is the uploaded
+        query_chunk_table, `prog` a nat.QueryProg, `isin` the sorted ISIN elements (uint8
+        device tensor or None); mask (int64 / uint64, nwords) and count (int32, nwords) are
+        written.  `arena` may be a raw device address."""
+        base = arena if isinstance(arena, int) else _ptr(arena)
+        rc = nat.lib().hsds_query_mask(self.eng.h, base, _ptr(chunks), int(nchunks), int(nwords), int(rowsize),
+                                       ctypes.byref(prog), _ptr(isin), 0 if isin is None else isin.numel(),
+                                       _ptr(mask), _ptr(count), _stream_handle(stream))
+        if rc != nat.OK:
+            raise nat.NativeError(rc, "hsds_query_mask")
+
+    def query_emit(self, arena, chunks, nchunks, nwords, rowsize, mask, base, limit, segs, out_elem, out,
+                   upd_segs=None, upd_elem=0, upd=None, stream=None):
+        """Asynchronous emit pass of a query (hsds_query_emit): `base` is the exclusive scan
+        (int64) of the mask pass's counts; response record r (out_elem bytes: uint64 dataset
+        index, then `segs`) goes to out + r * out_elem for every rank r < limit (0: all).
+        upd_segs / upd: the update record's segments and its bytes on the device."""
+        abase = arena if isinstance(arena, int) else _ptr(arena)
+        rc = nat.lib().hsds_query_emit(self.eng.h, abase, _ptr(chunks), int(nchunks), int(nwords), int(rowsize),
+                                       _ptr(mask), _ptr(base), int(limit), nat.point_segs(segs), len(segs),
+                                       int(out_elem), _ptr(out),
+                                       None if upd_segs is None else nat.point_segs(upd_segs),
+                                       0 if upd_segs is None else len(upd_segs), int(upd_elem), _ptr(upd),
+                                       _stream_handle(stream))
+        if rc != nat.OK:
+            raise nat.NativeError(rc, "hsds_query_emit")
+
+    def query(self, arena, chunks, rowsize, prog, isin, segs, out_elem, limit=0, upd_segs=None, upd_elem=0,
+              upd=None, stream=None):
+        """One query over many chunks: ONE mask launch, one scan (torch.cumsum) and ONE emit
+        launch.  `chunks`: (slot, first, count, step, index0) per chunk in dataset order --
+        the byte offset of the chunk array from `arena` (< 0: no such object), the selected
+        rows first + i * step for i < count, the dataset index of the chunk's row 0.
+        Returns (out, starts): the response records (uint8 device tensor, out_elem bytes
+        each, dataset order, at most `limit` when limit > 0) and the host int64 array of
+        nchunks + 1 running match counts before the limit (starts[k]: matches in the chunks
+        before k; starts[-1]: the total) -- the one wait for the device."""
+        table, nwords = query_chunk_table(chunks)
+        dev = self.device
+        nchunks = len(table)
+        if nwords == 0:
+            return torch.empty(0, dtype=torch.uint8, device=dev), np.zeros(nchunks + 1, np.int64)
+        d_table = torch.from_numpy(table.view(np.int64).reshape(-1)).to(dev)
+        d_isin = None if isin is None or len(isin) == 0 else torch.from_numpy(np.ascontiguousarray(isin)).to(dev)
+        mask = torch.empty(nwords, dtype=torch.int64, device=dev)
+        count = torch.empty(nwords, dtype=torch.int32, device=dev)
+        self.query_mask(arena, d_table, nchunks, nwords, rowsize, prog, d_isin, mask, count, stream=stream)
+        incl = torch.cumsum(count, 0, dtype=torch.int64)
+        base = incl - count
+        # running counts at the chunk boundaries: base[word0[k]], and the total
+        w0 = torch.from_numpy(np.minimum(table["word0"], nwords - 1)).to(dev)
+        starts = torch.cat([base[w0], incl[-1:]]).cpu().numpy()
+        starts[:-1][table["word0"] >= nwords] = starts[-1]
+        total = int(starts[-1])
+        nout = min(total, int(limit)) if limit and limit > 0 else total
+        out = torch.empty(nout * int(out_elem), dtype=torch.uint8, device=dev)
+        if nout:
+            self.query_emit(arena, d_table, nchunks, nwords, rowsize, mask, base, limit, segs, out_elem, out,
+                            upd_segs=upd_segs, upd_elem=upd_elem, upd=upd, stream=stream)
+        return out, starts
 
     def unshuffle(self, src, dst, itemsize, stream=None):
         rc = nat.lib().hsds_unshuffle_device(self.eng.h, _ptr(src), src.numel(), int(itemsize), _ptr(dst),

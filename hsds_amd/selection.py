@@ -833,3 +833,61 @@ def chunkWritePoints(chunk_id=None, chunk_layout=None, chunk_arr=None, point_arr
     slot = torch.zeros(1, dtype=torch.int64, device=eng.device)
     eng.scatter_points(d_chunk, slot, None, eoff, order, segs, dt.itemsize, val_dt.itemsize, d_vals)
     np.copyto(arr, d_chunk.cpu().numpy().view(dt).reshape(arr.shape))
+
+
+# ---- query selections (GET_Chunk / PUT_Chunk with query=, chunk_dn.py:192-240, 499-545) ---------
+def chunkQuery(chunk_id=None, chunk_layout=None, chunk_arr=None, slices=None, query=None, query_update=None,
+               select_dt=None, limit=0):
+    """chunkUtil.chunkQuery (chunkUtil.py:1375-1569): the rows of the selection `slices` of
+    the 1-D compound `chunk_arr` that match `query`, as an array of getQueryDtype(select_dt)
+    -- the uint64 dataset index, then the selected fields -- at most `limit` of them (0: all).
+    One mask launch, one scan and one emit launch on the GPU instead of numpy's eval.
+    None when a `where <field> in (...)` tail leaves no row, an empty array when only the
+    expression matches nothing.  query_update {field: value}: the matched rows (under the
+    limit) of chunk_arr get those values and are returned as updated.
+    Deviations from the reference (DESIGN.md "Query selections"): the parsed tree is
+    evaluated, not the raw text; the index of selection row i is offset + start + i * step
+    (the reference's is right only while every row matches); an update changes the matched
+    rows (the reference indexes chunk_arr with selection-relative indices)."""
+    from .engine import ChunkEngine
+    from . import query as qry
+    if not isinstance(chunk_arr, np.ndarray):
+        raise TypeError("unexpected array type")
+    if chunk_arr.ndim != 1:
+        raise ValueError("Query operations only supported on one-dimensional datasets")
+    dt = chunk_arr.dtype
+    n = chunk_arr.shape[0]
+    if not slices:
+        slices = [slice(0, n, 1)]
+    if len(slices) != 1:
+        raise ValueError("Selection rank does not match shape rank")
+    offset = getChunkCoordinate(chunk_id, chunk_layout)[0]
+    cq = qry.compile_query(query, dt)
+    if not cq.has_expr and not cq.where_field:
+        return None
+    upd_segs, upd = None, None
+    if query_update:
+        if cq.where_field:
+            raise ValueError("query update is not supported with where in")
+        upd_segs, upd = qry.update_record(dt, query_update)
+        if not chunk_arr.flags["C_CONTIGUOUS"]:
+            raise ValueError("chunk arrays are C-contiguous")
+    s = slices[0]
+    if s.step is not None and s.step < 1:
+        raise ValueError("query selections have a positive step")
+    start, stop, step = s.indices(n)
+    count = len(range(start, stop, step))
+    segs, rsp_dt = qry.query_segments(dt, select_dt)
+    eng = ChunkEngine()
+    d_chunk = _to_dev(chunk_arr, eng.device)
+    d_upd = None if upd is None else _to_dev(upd, eng.device)
+    out, starts = eng.query(d_chunk, [(0, start, count, step, offset)], dt.itemsize, cq.prog, cq.isin, segs,
+                            rsp_dt.itemsize, limit=limit, upd_segs=upd_segs, upd_elem=0 if upd is None else len(upd),
+                            upd=d_upd)
+    if cq.where_field and starts[-1] == 0:
+        return None
+    rsp = np.zeros(out.numel() // rsp_dt.itemsize, rsp_dt)
+    rsp.view(np.uint8).reshape(-1)[:] = out.cpu().numpy()
+    if upd is not None and len(rsp):
+        np.copyto(chunk_arr, d_chunk.cpu().numpy().view(dt).reshape(chunk_arr.shape))
+    return rsp

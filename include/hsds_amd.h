@@ -27,6 +27,10 @@
  *                           chunkUtil.py:793 getChunkRelativePoint
  *   hsds_points_gather   <- chunkUtil.py:998 chunkReadPoints, chunk_crawl.py:422-530 (placement by point index)
  *   hsds_points_scatter  <- chunkUtil.py:1064 chunkWritePoints
+ *   hsds_query_mask      <- chunkUtil.py:1375-1531 chunkQuery (the eval of the where clause, np.isin, the
+ *                           intersection), reached from GET_Chunk / PUT_Chunk with query= (chunk_dn.py:192-240, 499-545)
+ *   hsds_query_emit      <- chunkUtil.py:1527-1569 (limit, the update of matched rows, the response array of
+ *                           getQueryDtype, chunkUtil.py:1356-1372) and the SN's assembly (dset_lib.py:626-653)
  *
  * Threading: an engine is bound to one device and is re-entrant: its calls may come from
  * any host threads (a DN running them off the event loop in a thread pool).  Calls that
@@ -267,6 +271,84 @@ int hsds_points_gather(hsds_engine* e, const void* d_arena, const int64_t* d_slo
 int hsds_points_scatter(hsds_engine* e, void* d_arena, const int64_t* d_slot, const int64_t* d_which,
                         const int64_t* d_eoff, const int64_t* d_order, int64_t n, const hsds_point_seg* segs,
                         int nsegs, int chunk_elem, int out_elem, const void* d_vals, void* stream);
+
+/* ---- query selections ---------------------------------------------------------------
+ * Where-clause queries over 1-D compound datasets (GET_Chunk / PUT_Chunk with query=:
+ * chunk_dn.py:192-240, chunkUtil.chunkQuery chunkUtil.py:1375-1569) over chunks resident in
+ * device memory.  The predicate is a postfix program evaluated per row over a stack of bits;
+ * hsds_amd/query.py compiles it from the query text. */
+#define HSDS_QUERY_MAX_OPS 32
+#define HSDS_QUERY_POOL 256
+#define HSDS_QUERY_MAX_ISIN 1024
+enum { HSDS_Q_CONST = 0, HSDS_Q_CMP = 1, HSDS_Q_CMP_FIELD = 2, HSDS_Q_CMP_BYTES = 3, HSDS_Q_ISIN = 4,
+       HSDS_Q_AND = 5, HSDS_Q_OR = 6 };
+enum { HSDS_Q_EQ = 0, HSDS_Q_NE = 1, HSDS_Q_LT = 2, HSDS_Q_LE = 3, HSDS_Q_GT = 4, HSDS_Q_GE = 5 };
+/* the domain both sides of a comparison convert to; SU (CMP_FIELD only): A is a signed and B
+ * an unsigned integer, compared exactly as numpy compares int64 with uint64 */
+enum { HSDS_Q_DOM_I64 = 0, HSDS_Q_DOM_U64 = 1, HSDS_Q_DOM_F64 = 2, HSDS_Q_DOM_SU = 3 };
+/* field kinds: 0..3 int8/16/32/64, 4..7 uint8/16/32/64, 8 float32, 9 float64, 10 S<n> */
+enum { HSDS_Q_KIND_I1 = 0, HSDS_Q_KIND_U1 = 4, HSDS_Q_KIND_F4 = 8, HSDS_Q_KIND_F8 = 9, HSDS_Q_KIND_S = 10 };
+
+typedef struct {
+  uint8_t op;        /* HSDS_Q_*                                                              */
+  uint8_t cmp;       /* HSDS_Q_EQ ..                                                          */
+  uint8_t dom;       /* CMP / CMP_FIELD / ISIN of a number: the domain both sides convert to  */
+  uint8_t kind;      /* kind of field A                                                       */
+  uint8_t kind_b;    /* CMP_FIELD: kind of field B; CMP_BYTES: 1 when B is a field            */
+  uint8_t pad[3];
+  int32_t off;       /* byte offset of field A in the row                                     */
+  int32_t off_b;     /* CMP_FIELD: offset of field B; CMP_BYTES: offset of the constant in the
+                        pool (or of field B); ISIN: byte offset of the elements in the buffer */
+  int32_t len;       /* S fields: width of A                                                  */
+  int32_t len_b;     /* CMP_BYTES: bytes of the constant (width of field B)                   */
+  uint64_t imm;      /* CMP: the constant's bits in `dom`; CONST: 0 / 1; ISIN: element count  */
+} hsds_query_op;
+
+typedef struct {
+  int32_t nops;                          /* 1 .. HSDS_QUERY_MAX_OPS                           */
+  int32_t reserved;
+  hsds_query_op ops[HSDS_QUERY_MAX_OPS];
+  uint8_t pool[HSDS_QUERY_POOL];         /* bytes constants                                   */
+} hsds_query_prog;
+
+/* The selected rows of one chunk: rows first + i * step, i in [0, count), of the chunk array
+ * at d_arena + slot (slot < 0: no such object, the chunk matches nothing).  Row i has the
+ * dataset index index0 + first + i * step.  word0 = the chunk's first mask word: the sum of
+ * ceil(count / 64) over the chunks before it (rows are padded to whole 64-row words per
+ * chunk, so a word never spans two chunks). */
+typedef struct {
+  int64_t slot;
+  int64_t first;
+  int64_t count;
+  int64_t step;
+  int64_t index0;
+  int64_t word0;
+} hsds_query_chunk;
+
+/* The mask pass of chunkQuery (chunkUtil.py:1423-1525: eval(eval_str), np.isin and their
+ * intersection): evaluates `prog` on every selected row of d_chunks[0..nchunks) (rows of
+ * rowsize bytes); bit l of d_mask[w] = row 64 * (w - word0) + l of its chunk matches, and
+ * d_count[w] = popcount(d_mask[w]), for the nwords words of the table.  ISIN elements are
+ * sorted values in d_isin (isin_bytes bytes; 8 bytes each in the op's domain, or `len` bytes
+ * for an S field).  HSDS_ERR_ARG: a program that is too long, unbalanced, or reads outside
+ * the row, the pool or d_isin. */
+int hsds_query_mask(hsds_engine* e, const void* d_arena, const hsds_query_chunk* d_chunks, int64_t nchunks,
+                    int64_t nwords, int rowsize, const hsds_query_prog* prog, const void* d_isin, int64_t isin_bytes,
+                    uint64_t* d_mask, int32_t* d_count, void* stream);
+
+/* The response of chunkQuery (chunkUtil.py:1527-1569) for all chunks at once: d_base is the
+ * exclusive scan of d_count; the matching row of rank r = d_base[w] + popcount(d_mask[w]
+ * below its lane) < limit (limit 0: no limit) becomes response record r at d_out + r *
+ * out_elem: its uint64 dataset index, then the table's segments of the row (out_off >= 8:
+ * the fields packed as chunkUtil.getQueryDtype packs them, chunkUtil.py:1356-1372).
+ * Update mode (upd_segs != NULL; PUT_Chunk with a query, chunk_dn.py:192-240,
+ * chunkUtil.py:1473-1545): bytes [out_off, out_off + nbytes) of the value record d_upd
+ * (upd_elem bytes) are first stored to [chunk_off, ..) of every such row, which is then
+ * emitted as updated. */
+int hsds_query_emit(hsds_engine* e, void* d_arena, const hsds_query_chunk* d_chunks, int64_t nchunks,
+                    int64_t nwords, int rowsize, const uint64_t* d_mask, const int64_t* d_base, int64_t limit,
+                    const hsds_point_seg* segs, int nsegs, int out_elem, void* d_out,
+                    const hsds_point_seg* upd_segs, int n_upd_segs, int upd_elem, const void* d_upd, void* stream);
 
 /* ---- host response buffers (the "no gather" sharded read) ---------
  * The SN streams each page of a GET_Value to the client (chunk_sn.py:1085-1135): the
